@@ -14,7 +14,14 @@ shard with no data-path collective and the 64-B records are gathered to rank 0 (
 moment sums do not depend on the shard (fixed sample units), so the gathered
 records equal the 1-GPU run's bit for bit.  `--scaling weak` keeps 1e5 series per rank instead.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0: the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`), the per-kernel
+HIP-event times of the timed steps and the roofline and fit statistics computed from them.
+`--dump-outputs DIR` also writes the last timed step's records as DIR/<field>.npy.  `--full` adds
+every block that takes runs of its own: the all-f64 moment kernel, the C4 rank rehearsal, the
+sustained run, the C2 exposure, the CPU-oracle baseline with its parity check and reference
+ceiling, and the C5 faint exposure with its Float32 sweep (each still switched off by its
+`--no-*` option).
 """
 from __future__ import annotations
 
@@ -46,6 +53,12 @@ def parse():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"])
     ap.add_argument("--dump-records", default=None,
                     help="rank 0 writes the gathered records (.npy, PARAM_DTYPE) here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the records of the last timed step (what a caller of "
+                         "the timed path receives) as DIR/<field>.npy, Float64, in series order")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the blocks beside the headline: all-f64 moments, C4 rank "
+                         "rehearsal, sustained run, C2 exposure, CPU baseline + parity, C5")
     ap.add_argument("--no-f64", action="store_true",
                     help="skip the all-f64 moment-kernel (option mix = 0) comparison steps")
     ap.add_argument("--samples", type=int, default=100_000)
@@ -240,9 +253,12 @@ def main():
         if dist:
             dist.destroy_process_group()
         return
-    if args.dump_records:
+    if args.dump_records or args.dump_outputs:
         recs = (gathered if use_dist else params).cpu().numpy().reshape(-1).view(gpd.PARAM_DTYPE)
-        np.save(args.dump_records, recs)
+        if args.dump_records:
+            np.save(args.dump_records, recs)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, recs)
 
     # --- roofline of the dominant kernel (harmonic moment pass) ---------------------------
     rec = gpd.PARAM_DTYPE
@@ -284,7 +300,8 @@ def main():
     # the same steps with every harmonic on the f64 MFMAs (option mix = 0; the production kernel puts
     # harmonics 17..24 on split-bf16 MFMAs), untimed by the headline
     f64_all = None
-    if not args.no_f64 and world == 1:
+    full = args.full
+    if full and not args.no_f64 and world == 1:
         log("all-f64 moment kernel comparison steps (option mix = 0)")
         gpd.set_option("mix", 0)
         try:
@@ -312,7 +329,7 @@ def main():
     # the resident batch, a view — its records equal the batch's bit for bit, tests/test_gpu_c4.py),
     # timed the same way; the driver measures the 8-GPU run itself
     c4 = None
-    if (world == 1 and (P_total, N) == (100_000, 100_000) and args.scaling == "strong"
+    if (full and world == 1 and (P_total, N) == (100_000, 100_000) and args.scaling == "strong"
             and not args.no_c4):
         n8 = shard.shard_counts(P_total, 8)[0]
         fo8 = fcop[:n8].contiguous()
@@ -346,7 +363,7 @@ def main():
     sustained = None
     sustain = args.sustain if args.sustain is not None else (
         8.0 if (P_total, N) == (100_000, 100_000) else 0.0)
-    if world == 1 and sustain > 0:
+    if full and world == 1 and sustain > 0:
         chunks, n_done, ts = [], 0, time.perf_counter()
         while time.perf_counter() - ts < sustain:
             tc = time.perf_counter()
@@ -365,11 +382,11 @@ def main():
     # BASELINE configs[1] (C2): one exposure through the drop-in call as the reference makes it
     # (host arrays in, output = copy(data) back), PCIe included
     c2 = None
-    if world == 1 and not args.no_c2 and P >= 32 and not c32:
+    if full and world == 1 and not args.no_c2 and P >= 32 and not c32:
         c2 = c2_block(gpd, t, d, fc, args, log)
 
     cpu = None
-    if not args.no_cpu and args.cpu_pixels > 0 and world == 1:  # rank 0 at N=1 only
+    if full and not args.no_cpu and args.cpu_pixels > 0 and world == 1:  # rank 0 at N=1 only
         cpu = cpu_baseline(gpd, t, d, fc, fcop, par, args, N,
                            par64=None if f64_all is None else f64_all["records"])
     if f64_all is not None:
@@ -378,7 +395,7 @@ def main():
     # BASELINE configs[4] (C5): one faint exposure, GPU step + CPU oracle sample (after the C3
     # batch is released: the exposure needs 8 GB more)
     c5 = None
-    if (world == 1 and not args.no_c5 and (P_total, N) == (100_000, 100_000)
+    if (full and world == 1 and not args.no_c5 and (P_total, N) == (100_000, 100_000)
             and args.scaling == "strong"):
         del d, fc
         torch.cuda.synchronize(dev)
@@ -414,6 +431,21 @@ def main():
     print(json.dumps(out))
     if dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, recs):
+    """The records of the last timed step, one Float64 array per field and one entry per series
+    (in series order; the complex fields as (P, 2) = re, im): what a caller of the timed path
+    receives.  The inputs depend on the arguments alone (seeded counter RNG), so two builds run
+    with the same arguments can be compared array for array."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name in recs.dtype.names:
+        x = np.ascontiguousarray(recs[name])
+        if np.iscomplexobj(x):
+            x = x.view(np.float64).reshape(-1, 2)
+        np.save(os.path.join(path, name + ".npy"), x.astype(np.float64))
 
 
 def c2_block(gpd, t, d, fc, args, log, reps=5):

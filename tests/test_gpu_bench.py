@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_json_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pixels", "512",
                         "--samples", "8192", "--steps", "2", "--warmup", "1", "--cpu-pixels", "16",
-                        "--sustain", "0.3"],
+                        "--sustain", "0.3", "--full"],
                        capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -58,6 +58,32 @@ def _run_bench(nproc, extra, tmp, tag, backend="gloo", launcher=None):
     assert len(lines) == 1
     import numpy as np
     return json.loads(lines[0]), np.load(dump)
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: the blocks with runs of their
+    own are absent from the line.  --dump-outputs writes the last timed step's records, one
+    Float64 array per field in series order, the same from run to run (seeded inputs)."""
+    import numpy as np
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    out, rec = _run_bench(1, ["--dump-outputs", dirs[0], "--steps", "3"], str(tmp_path), "a")
+    _run_bench(1, ["--dump-outputs", dirs[1], "--steps", "3"], str(tmp_path), "b")
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["value"] == pytest.approx(520 * 4096 / (out["ms_per_step"] * 1e-3), rel=1e-9)
+    for key in ("cpu_baseline", "all_f64_moments", "c4_rank_rehearsal", "sustained", "c2_exposure",
+                "c5_faint"):
+        assert out[key] is None, key
+    assert out["roofline"]["avg_ms"] > 0 and out["kernels_ms"]["moments"] > 0
+    assert sorted(os.listdir(dirs[0])) == sorted(f + ".npy" for f in rec.dtype.names)
+    for f in rec.dtype.names:
+        a, b = (np.load(os.path.join(d, f + ".npy")) for d in dirs)
+        assert a.dtype == np.float64 and a.shape[0] == 520
+        assert a.tobytes() == b.tobytes(), f
+        want = np.ascontiguousarray(rec[f])
+        if f in ("a", "c"):
+            want = want.view(np.float64).reshape(520, 2)
+        assert np.array_equal(a, want.astype(np.float64)), f
+    assert np.isfinite(np.load(os.path.join(dirs[0], "b.npy"))).all()
 
 
 @pytest.mark.parametrize("nproc", [2, 3, 4])

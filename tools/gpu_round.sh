@@ -19,7 +19,7 @@ for s in $STEPS; do
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 ;;
     bench)
-      timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+      timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
     prof)
       timeout -k 10 900 bash tools/profile.sh "$TAG" > "$OUT/prof_files.txt" 2>&1 ;;
     *) echo "unknown step $s" >&2; exit 2 ;;
