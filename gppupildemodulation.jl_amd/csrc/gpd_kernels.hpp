@@ -1604,6 +1604,11 @@ __global__ __launch_bounds__(512, 1) void k_moments_ws(Problem pb, const double 
     for (int i = 0; i < ntiles; ++i) {
         const double *qd = (const double *)qs[i & 1];
         const double *tb = ts[i & 1];
+        // mm_phys swizzles bit 3 of the series on s & 1 = fk & 1: it swaps the series blocks m
+        // and m ^ 1 in the lanes of an odd fk.  The A fragment of block m at K-step 0 is block
+        // m ^ (fk & 1) of row fk: one base for the even m, one for the odd m.
+        const double *qa0 = qd + 2 * (fk * MM_ROW + wave * 32 + ppair + 8 * (fk & 1)) + comp;
+        const double *qa1 = qd + 2 * (fk * MM_ROW + wave * 32 + ppair - 8 * (fk & 1)) + comp;
         bool live = true;  // FAINT: the tile holds a valid sample
         if constexpr (FAINT) {
             const int ds = __builtin_amdgcn_readfirstlane(tds[i & 1]);
@@ -1618,8 +1623,11 @@ __global__ __launch_bounds__(512, 1) void k_moments_ws(Problem pb, const double 
         }
         auto ldfrag = [&](int ks, double (&a)[4], double (&b)[NC]) {
             const int k = ks * 4 + fk;
+            // a[m] = qd[2 * mm_phys(wave * 32 + m * 8 + ppair, k) + comp], from the two lane
+            // bases: every read is base + constant, so pairs merge into ds_read2_b64 (written
+            // per read, each address takes a VALU add of its own and the reads stay single)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) a[m] = qd[2 * mm_phys(wave * 32 + m * 8 + ppair, k) + comp];
+            for (int m = 0; m < 4; ++m) a[m] = ((m & 1) ? qa1 : qa0)[2 * (ks * 4 * MM_ROW + m * 8)];
 #pragma unroll
             for (int n = 0; n < NC; ++n) b[n] = tb[k * 2 * KH + n * 16 + fi];
         };
